@@ -13,10 +13,18 @@ step i overlaps the VALU-bound update of step i+1; --pipeline-depth 1 gives the 
 
 metric / value: coded symbols (incl. tail, the reference's definition scripts/tabulate_data.py:33) decoded per
 second over the whole job, Msymbols/s.  The JSON line also carries the ACS-update-only and chainback-only
-rates from HIP events recorded by the library on the streams its kernels run on (vhip_enable_timing), the HBM
-roofline of the dominant (ACS) kernel, and a CPU baseline timed on this host.
+rates from HIP events recorded by the library on the streams its kernels run on (vhip_enable_timing) during the
+timed steps.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the outputs of the last
+step if --dump-outputs is given, print the line.  --full adds everything else, each after the timed region: the
+bit-error check, the HBM roofline of the dominant (ACS) kernel (with passes of its own), the replayed counters, a
+CPU baseline timed on this host and, for the default workload, the other single-GPU configurations and the
+one-frame latency figures under "extra".
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   # DIR/decoded.npy: the last step's decoded bytes
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 """
 import argparse
@@ -197,9 +205,15 @@ class HipShard:
         nout = 2 if self.depth > 1 else 1
         self.d_out = [torch.zeros(frames * self.payload_bytes, dtype=torch.uint8, device=dev) for _ in range(nout)]
         self.timed_from = None
+        # a Namespace without these (the tests build their own) gets the full statistics and no output copy
+        self.full = getattr(args, "full", True)
+        self.keep_output = bool(getattr(args, "dump_outputs", None))
+        self.last_pass = None
+        self.last_output = None
 
     def one_pass(self, i):
         sc, oc = self.chunk * self.nsteps * self.spec.R, self.chunk * self.payload_bytes
+        self.last_pass = i
         out = self.d_out[i % len(self.d_out)]
         for c in range(self.nchunks):
             if self.windowed:
@@ -216,8 +230,14 @@ class HipShard:
             self.timed_from = True
 
     def stats(self):
-        su, nu, sc, nc = self.dec.read_timing()
+        su, nu, sc, nc = self.dec.read_timing()  # also waits for the handle to go idle
         passes = max(1, nu // self.nchunks)
+        if self.keep_output:
+            # the decoded bytes of the last timed pass, taken before anything below reuses the output buffers
+            self.last_output = self.d_out[self.last_pass % len(self.d_out)].cpu().numpy().reshape(self.frames, self.payload_bytes)
+        if not self.full:
+            return {"units_per_pass": self.frames * self.nsteps * self.spec.R, "bit_errors": -1, "update_ms": su / passes,
+                    "chainback_ms": sc / passes, "timed_update_launches": nu, "variant": self.dec.variant}
         nerr = -1
         if self.spec.K == 24 and self.nchunks == 1:
             # the timed chainback is the harness's own call (nbits = payload bits), which does not decode K=24 correctly
@@ -282,27 +302,12 @@ def replayed_counter(kind, code, family):
 
 # ------------------------------------------------------------------------------------------------ one JSON object per workload
 def report(args, spec, frames, core, shard, with_cpu, cpu_budget):
-    """The bench line of one workload from the job loop's core figures and the shard's kernel timings."""
+    """The bench line of one workload from the job loop's core figures and the shard's kernel timings; with --full also the
+    bit errors, the roofline, the replayed counters and (with_cpu) the CPU baseline."""
     st = core.pop("stats")
     n_gpus, nsteps, payload_bits = core["n_gpus"], shard.nsteps, shard.payload_bits
     upd_ms, cb_ms = st["update_ms"], st["chainback_ms"]
     variant = st["variant"]
-    family = kernel_family(spec.K)
-    abytes = algorithmic_bytes_per_frame_step(spec) * frames * nsteps  # per pass of one rank (SURVEY.md §8d)
-    mbytes = moved_bytes_per_frame_step(spec, variant, {4: 5, 5: 2}.get(variant)) * frames * nsteps
-    achieved = mbytes / (upd_ms * 1e-3) / 1e9
-    tv, tsrc = replayed_counter("traffic", args.code, family)
-    vv, vsrc = replayed_counter("valu", args.code, family)
-    valu = None
-    if vv is not None:
-        # instructions per launch come from the committed PMC pass; the time is this run's
-        rate = vv["valu_wave_instr_per_launch"] / (upd_ms * 1e-3) / 1e9
-        valu = {"wave_instr_per_launch": vv["valu_wave_instr_per_launch"], "achieved_ginstr_per_s": round(rate, 2),
-                "issue_ceiling_ginstr_per_s": round(vv["issue_ceiling_ginstr_per_s"], 2),
-                "frac": round(rate / vv["issue_ceiling_ginstr_per_s"], 4),
-                # the same kernel with nothing else on the device (roofline.alone)
-                "frac_alone": round(vv["valu_wave_instr_per_launch"] / (st["update_ms_alone"] * 1e-3) / 1e9 / vv["issue_ceiling_ginstr_per_s"], 4),
-                "source": vsrc}
     out = {
         "metric": f"Msymbols/s decoded, K={spec.K} r=1/{spec.R} " + ("(fused sliding-window decode: NOT the reference chainback semantics)" if shard.windowed else "(init + ACS update + chainback)"),
         "value": round(core["value"] / 1e6, 6),
@@ -327,8 +332,28 @@ def report(args, spec, frames, core, shard, with_cpu, cpu_budget):
         "chainback_ms": round(cb_ms, 4),
         "kernel_timing": "HIP events recorded by the library around its launches, on the streams they run on, timed region only"
                          + ("; update and chainback of consecutive steps overlap (pipeline depth 2), so the two do not add up to ms_per_step" if shard.depth > 1 else ""),
-        "bit_errors": int(core["bit_errors"]),
         "payload_bits_total": frames * payload_bits * n_gpus,
+    }
+    if not shard.full:
+        return out
+    family = kernel_family(spec.K)
+    abytes = algorithmic_bytes_per_frame_step(spec) * frames * nsteps  # per pass of one rank
+    mbytes = moved_bytes_per_frame_step(spec, variant, {4: 5, 5: 2}.get(variant)) * frames * nsteps
+    achieved = mbytes / (upd_ms * 1e-3) / 1e9
+    tv, tsrc = replayed_counter("traffic", args.code, family)
+    vv, vsrc = replayed_counter("valu", args.code, family)
+    valu = None
+    if vv is not None:
+        # instructions per launch come from the committed PMC pass; the time is this run's
+        rate = vv["valu_wave_instr_per_launch"] / (upd_ms * 1e-3) / 1e9
+        valu = {"wave_instr_per_launch": vv["valu_wave_instr_per_launch"], "achieved_ginstr_per_s": round(rate, 2),
+                "issue_ceiling_ginstr_per_s": round(vv["issue_ceiling_ginstr_per_s"], 2),
+                "frac": round(rate / vv["issue_ceiling_ginstr_per_s"], 4),
+                # the same kernel with nothing else on the device (roofline.alone)
+                "frac_alone": round(vv["valu_wave_instr_per_launch"] / (st["update_ms_alone"] * 1e-3) / 1e9 / vv["issue_ceiling_ginstr_per_s"], 4),
+                "source": vsrc}
+    out.update({
+        "bit_errors": int(core["bit_errors"]),
         # achieved = bytes the ACS kernels move per pass / their event-timed duration; for K <= 15 that IS the
         # algorithmic figure of SURVEY.md §8d, for the multi-step K=24 passes it is what the passes really move
         "roofline": {"bound": "hbm", "kernel": "acs_update", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
@@ -346,7 +371,7 @@ def report(args, spec, frames, core, shard, with_cpu, cpu_budget):
                                "chainback_ms": round(st["chainback_ms_alone"], 4)}},
         # the binding limit of the K<=15 ACS kernels: packed-integer VALU issue, not HBM
         "valu_issue": valu,
-    }
+    })
     if with_cpu:
         out["cpu_baseline"] = cpu_baseline(spec, payload_bits, cpu_budget)
     return out
@@ -360,7 +385,7 @@ EXTRA_CONFIGS = [("615", 10, 2, 4.0), ("224", 10, 2, 1.0)]  # (code, steps, warm
 def run_extra_config(base_args, code, steps, warmup, cpu_budget, dev):
     args = argparse.Namespace(**vars(base_args))
     args.code, args.frames, args.payload_bits, args.variant, args.chunk_frames, args.windowed = code, None, None, 0, None, False
-    args.ebn0, args.hard = None, False
+    args.ebn0, args.hard, args.dump_outputs = None, False, None
     spec = C.CODES[code]
     frames = DEFAULT_FRAMES[spec.K]
     holder = {}
@@ -434,6 +459,21 @@ def one_frame_handles(budget_s=0.4):
     return rows
 
 
+DUMP_BYTES = 32 << 20  # what --dump-outputs may write (float32)
+
+
+def dump_outputs(out_dir, decoded):
+    """DIR/decoded.npy: the decoded bytes [frames, payload bytes] of this rank's last timed step as float32 -- every frame while
+    that fits DUMP_BYTES, else a fixed seeded sample of whole frames in frame order (the same frames on every run)."""
+    frames, nbytes = decoded.shape
+    keep = max(1, DUMP_BYTES // (4 * nbytes))
+    if frames > keep:
+        decoded = decoded[np.sort(np.random.default_rng(0x5EED).choice(frames, keep, replace=False))]
+    decoded = decoded[:, :max(1, DUMP_BYTES // 4)]  # one frame larger than the budget: its leading bytes
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "decoded.npy"), decoded.astype(np.float32))
+
+
 # BASELINE.json configs: K=7 x 65536 frames, K=15 x 4096 frames, K=24 single long frame; K=9 sized in between
 DEFAULT_FRAMES = {7: 65536, 9: 32768, 15: 4096, 24: 1}
 
@@ -458,8 +498,13 @@ def main():
     ap.add_argument("--windowed", action="store_true", help="K<=9: time the fused sliding-window decode (one kernel, no decision history in HBM) "
                                                             "instead of init + update + chainback; results are NOT those of the reference chainback")
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    ap.add_argument("--no-extra-configs", action="store_true", help="only the headline workload (default: at N=1 with the default workload, BASELINE "
-                                                                    "configs[2] K=15 x 4096 and configs[3] K=24 x 1 follow under extra.configs)")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full, only the headline workload (default: at N=1 with the default "
+                                                                    "workload, BASELINE configs[2] K=15 x 4096 and configs[3] K=24 x 1 follow "
+                                                                    "under extra.configs)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also measure and check everything beyond the headline: bit "
+                                                        "errors, roofline (with passes of its own), CPU baseline, the extra configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the decoded bytes of the last timed step to DIR/decoded.npy "
+                                                                        "(float32, a fixed sample of frames when the batch exceeds 32 MiB)")
     args = ap.parse_args()
     if args.no_pipeline:
         args.pipeline_depth = 1
@@ -499,11 +544,13 @@ def main():
     shard = holder["shard"]
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, shard.last_output)
         out = report(args, spec, frames, core, shard, core["n_gpus"] == 1 and not args.no_cpu_baseline, args.cpu_budget)
     shard.close()
     del holder["shard"], shard
     default_workload = args.code == "27" and args.frames is None and args.payload_bits is None and not args.windowed and args.variant == 0
-    if rank == 0 and world == 1 and default_workload and not args.no_extra_configs:
+    if rank == 0 and world == 1 and default_workload and args.full and not args.no_extra_configs:
         torch.cuda.empty_cache()
         extras = []
         for code, steps, warmup, cpu_budget in EXTRA_CONFIGS:

@@ -1,6 +1,9 @@
 """ctypes access to the CPU oracle (oracle/liboracle.so) and, when built, the compiled reference
-(oracle/_ref/libref.so, oracle/_ref/libref_ka9q615_w32.so).  Test infrastructure only."""
+(oracle/_ref/libref.so, oracle/_ref/libref_ka9q615_w32.so).  Where oracle/_ref is not built, reference_decoder()
+replays what the reference returned, recorded in tests/golden/oracle_vs_reference.npz.  Test infrastructure only."""
+import atexit
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -186,6 +189,173 @@ class RefDecoder:
 
     def __del__(self):
         self.close()
+
+
+# ------------------------------------------------------------------------------------------------ recorded reference
+# Every call on a reference decoder is keyed by what was done to that decoder before it (create arguments, init, update with
+# its symbols) and by the call itself, so a recording does not depend on test names or order.  Decision rows and metrics are
+# kept as SHA-256 digests (dtype, shape, contents), decoded bytes and return codes as they are.
+#   ORACLE_REF_RECORD=1 python -m pytest tests/test_oracle_vs_reference.py    (needs oracle/_ref) rewrites the recording
+REF_RECORD = os.path.join(ROOT, "tests", "golden", "oracle_vs_reference.npz")
+_recorded = None
+_recording = {}
+_record_saved_at_exit = []
+
+
+def digest(a):
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).digest()
+
+
+class Digest:
+    """An array the reference returned, as its digest()."""
+
+    def __init__(self, d):
+        self.d = bytes(d)
+
+
+def same(a, b):
+    """np.array_equal; where one side (or both) is a recorded Digest, equality of the digests."""
+    da = a.d if isinstance(a, Digest) else None
+    db = b.d if isinstance(b, Digest) else None
+    if da is None and db is None:
+        return np.array_equal(a, b)
+    return (da if da is not None else digest(a)) == (db if db is not None else digest(b))
+
+
+def _load_recording():
+    global _recorded
+    if _recorded is None:
+        z = np.load(REF_RECORD, allow_pickle=False)
+        keys, off, blob = z["keys"], z["offsets"], z["blob"].tobytes()
+        _recorded = {str(k): blob[off[i]:off[i + 1]] for i, k in enumerate(keys)}
+    return _recorded
+
+
+def _save_recording():
+    keys = sorted(_recording)
+    vals = [_recording[k] for k in keys]
+    off = np.zeros(len(vals) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(v) for v in vals])
+    np.savez_compressed(REF_RECORD, keys=np.array(keys), offsets=off, blob=np.frombuffer(b"".join(vals), dtype=np.uint8))
+
+
+def _int(v):
+    return int(np.frombuffer(v, dtype=np.int64)[0])
+
+
+class _Keyed:
+    def _start(self, code, poly, length, w32):
+        self._state = hashlib.sha256(repr(("create", int(code), [int(p) for p in poly], int(length), bool(w32))).encode()).digest()
+
+    def _advance(self, what, syms=None):
+        h = hashlib.sha256(self._state + repr(what).encode())
+        if syms is not None:
+            h.update(np.ascontiguousarray(syms, dtype=np.uint8).tobytes())
+        self._state = h.digest()
+
+    def _key(self, what):
+        return hashlib.sha256(self._state + repr(what).encode()).hexdigest()[:32]
+
+
+class RecordingRef(_Keyed):
+    """The live reference decoder, each result also written to the recording (ORACLE_REF_RECORD=1)."""
+
+    def __init__(self, code, poly, length, w32=False):
+        self.r = RefDecoder(code, poly, length, w32=w32)
+        self._start(code, poly, length, w32)
+
+    def init(self, start=0):
+        rc = self.r.init(start)
+        _recording[self._key(("init", int(start)))] = np.int64(rc).tobytes()
+        self._advance(("init", int(start)))
+        return rc
+
+    def update(self, syms, nbits):
+        self.r.update(syms, nbits)
+        self._advance(("update", int(nbits)), syms)
+
+    def chainback(self, nbits, endstate=0):
+        data, rc = self.r.chainback(nbits, endstate)
+        _recording[self._key(("chainback", int(nbits), int(endstate)))] = np.int64(rc).tobytes() + data.tobytes()
+        return data, rc
+
+    def rows(self, nrows):
+        a = self.r.rows(nrows)
+        _recording[self._key(("rows", int(nrows)))] = digest(a)
+        return a
+
+    def metrics(self):
+        a = self.r.metrics()
+        _recording[self._key(("metrics",))] = digest(a)
+        return a
+
+    def close(self):
+        self.r.close()
+
+
+class RecordedRef(_Keyed):
+    """What the reference decoder returned for the same calls, from tests/golden/oracle_vs_reference.npz."""
+
+    def __init__(self, code, poly, length, w32=False):
+        self.rec = _load_recording()
+        self._start(code, poly, length, w32)
+
+    def _get(self, what):
+        k = self._key(what)
+        if k not in self.rec:
+            raise KeyError(f"no recorded reference result for {what} after these calls: rerun with ORACLE_REF_RECORD=1 where oracle/_ref is built")
+        return self.rec[k]
+
+    def init(self, start=0):
+        rc = _int(self._get(("init", int(start))))
+        self._advance(("init", int(start)))
+        return rc
+
+    def update(self, syms, nbits):
+        self._advance(("update", int(nbits)), syms)
+
+    def chainback(self, nbits, endstate=0):
+        v = self._get(("chainback", int(nbits), int(endstate)))
+        return np.frombuffer(v[8:], dtype=np.uint8).copy(), _int(v[:8])
+
+    def rows(self, nrows):
+        return Digest(self._get(("rows", int(nrows))))
+
+    def metrics(self):
+        return Digest(self._get(("metrics",)))
+
+    def close(self):
+        pass
+
+
+def _recording_on():
+    if not (os.environ.get("ORACLE_REF_RECORD") and have_ref()):
+        return False
+    if not _record_saved_at_exit:
+        atexit.register(_save_recording)
+        _record_saved_at_exit.append(True)
+    return True
+
+
+def reference_decoder(code, poly, length, w32=False):
+    """The reference decoder: live where oracle/_ref is built (and recorded with ORACLE_REF_RECORD=1), else replayed."""
+    if _recording_on():
+        return RecordingRef(code, poly, length, w32=w32)
+    if have_ref():
+        return RefDecoder(code, poly, length, w32=w32)
+    return RecordedRef(code, poly, length, w32=w32)
+
+
+def ref_sizeof_long(w32=False):
+    """sizeof(long) as the reference objects were compiled (recorded alongside the calls)."""
+    key = f"sizeof_long_w32={int(bool(w32))}"
+    if have_ref():
+        v = ref(w32).ref_sizeof_long()
+        if _recording_on():
+            _recording[key] = np.int64(v).tobytes()
+        return v
+    return _int(_load_recording()[key])
 
 
 def encode(K, R, poly, payload):

@@ -204,7 +204,8 @@ def test_bench_two_ranks_rehearsal_on_one_gpu():
     F, bits, ebn0 = 4096, 512, 2.0
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--code", "27", "--frames", str(F), "--payload-bits", str(bits), "--ebn0", str(ebn0), "--no-cpu-baseline", "--no-extra-configs"]
+           "--code", "27", "--frames", str(F), "--payload-bits", str(bits), "--ebn0", str(ebn0), "--no-cpu-baseline", "--no-extra-configs",
+           "--full"]
     env = dict(os.environ, VITERBI_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]

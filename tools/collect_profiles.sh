@@ -20,7 +20,7 @@ mkdir -p $O $P
 cd /tmp && export TMPDIR=/tmp
 prof() { # name, code, extra bench args...
   local name=$1 code=$2; shift 2
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$name -o s --output-format csv -- python3 $R/bench.py --code $code --no-cpu-baseline "$@" > $O/stats_$name.json 2> $O/stats_$name.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/stats_$name -o s --output-format csv -- python3 $R/bench.py --code $code --full --no-cpu-baseline "$@" > $O/stats_$name.json 2> $O/stats_$name.err
   cp $O/stats_$name/s_kernel_stats.csv $P/${TAG}_${name}_kernel_stats.csv 2>/dev/null
   tail -n 1 $O/stats_$name.json > $P/${TAG}_${name}_bench_under_rocprof.json
   echo "stats $name done"
@@ -35,7 +35,7 @@ prof viterbispiral615 spiral615 --steps 5 --warmup 1
 prof viterbi224 224 --steps 5 --warmup 1
 pmc() { # name, code, counters...
   local name=$1 code=$2; shift 2
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d $O/pmc_$name -o c --output-format csv -- python3 $R/bench.py --code $code --no-cpu-baseline --no-extra-configs --no-pipeline --steps 2 --warmup 1 > $O/pmc_$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc "$@" -d $O/pmc_$name -o c --output-format csv -- python3 $R/bench.py --code $code --full --no-cpu-baseline --no-extra-configs --no-pipeline --steps 2 --warmup 1 > $O/pmc_$name.log 2>&1
   echo "pmc $name done"
 }
 for c in 27 615 224; do
@@ -70,15 +70,15 @@ cd $R
 python3 tools/sweep.py --out $P/${TAG}_sweep --steps 20 --cpu > $O/sweep.log 2>&1
 echo "sweep done"
 : > $P/${TAG}_config5_shard_size.jsonl
-for c in 27 47 29 49; do python3 bench.py --code $c --frames 131072 --steps 5 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl; done
-python3 bench.py --code 615 --frames 131072 --steps 2 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl
-python3 bench.py --code 224 --frames 12 --payload-bits 64 --steps 2 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl
+for c in 27 47 29 49; do python3 bench.py --code $c --frames 131072 --steps 5 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl; done
+python3 bench.py --code 615 --frames 131072 --steps 2 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl
+python3 bench.py --code 224 --frames 12 --payload-bits 64 --steps 2 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_config5_shard_size.jsonl
 echo "shard-size lines done"
 : > $P/${TAG}_windowed_decode.jsonl
-for c in 27 47 29 49; do python3 bench.py --code $c --windowed --steps 20 --warmup 3 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl; done
-for c in 615 spiral615; do python3 bench.py --code $c --windowed --steps 5 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl; done
-python3 bench.py --code 615 --windowed --frames 131072 --steps 1 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl
-python3 bench.py --code 27 --windowed --frames 1048576 --steps 3 --warmup 1 --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl
+for c in 27 47 29 49; do python3 bench.py --code $c --windowed --steps 20 --warmup 3 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl; done
+for c in 615 spiral615; do python3 bench.py --code $c --windowed --steps 5 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl; done
+python3 bench.py --code 615 --windowed --frames 131072 --steps 1 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl
+python3 bench.py --code 27 --windowed --frames 1048576 --steps 3 --warmup 1 --full --no-cpu-baseline 2>> $O/shard.err | tail -n 1 >> $P/${TAG}_windowed_decode.jsonl
 echo "windowed lines done"
 ./harness/viterbi_bench -t 1.0 -n 8 -o $P/${TAG}_harness_default.json > $O/harness.log 2>&1
 ./harness/viterbi_bench -t 1.0 -n 8 --host-api --hard -o $P/${TAG}_harness_host_1frame.json >> $O/harness.log 2>&1

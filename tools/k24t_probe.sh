@@ -10,6 +10,6 @@ O=$R/gpurun_out/${1:-k24t_probe}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for m in ${MODES:-0 1 2 3}; do
-  VHIP_K24T_MODE=$m timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/mode$m -o s --output-format csv -- python3 $R/bench.py --code 224 --no-cpu-baseline --steps 2 --warmup 1 > $O/mode$m.log 2>&1
+  VHIP_K24T_MODE=$m timeout -k 10 200 rocprofv3 --kernel-trace --stats -d $O/mode$m -o s --output-format csv -- python3 $R/bench.py --code 224 --full --no-cpu-baseline --steps 2 --warmup 1 > $O/mode$m.log 2>&1
   echo "mode $m:"; grep -E "pass_[hl]_kernel<true" $O/mode$m/s_kernel_stats.csv | awk -F'","' '{print substr($1,1,60), "calls", $2, "avg_ns", $4, "max_ns", $7}'
 done

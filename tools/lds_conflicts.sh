@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() { # name, bench args...
   local name=$1; shift
-  timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES -d $O/$name -o c --output-format csv -- python3 $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O/$name.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES -d $O/$name -o c --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --steps 2 --warmup 1 "$@" > $O/$name.log 2>&1
   python3 - <<PY
 import csv,collections
 rows=list(csv.DictReader(open("$O/$name/c_counter_collection.csv")))

@@ -19,7 +19,7 @@ def main():
     args = ap.parse_args()
     lines = []
     for code in args.codes.split(","):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--code", code, "--steps", str(args.steps), "--warmup", "3", "--no-extra-configs"]
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--code", code, "--steps", str(args.steps), "--warmup", "3", "--full", "--no-extra-configs"]
         if not args.cpu:
             cmd.append("--no-cpu-baseline")
         r = subprocess.run(cmd, capture_output=True, text=True)
